@@ -13,6 +13,9 @@ Workload (BASELINE.json metric: queries/s + p50 latency, 100M x 384 index, batch
     exact fallback); for N>1 the per-shard top-k lists are all-gathered over RCCL and merged by
     dawn_topk_merge_device on every rank;
   * `value` = queries per second over the timed K steps (max over ranks).
+  * `ms_per_step` = milliseconds of one timed step; `--dump-outputs DIR` writes what the last timed step of the
+    headline leg returned (labels, distances, found) as DIR/*.npy — the inputs are seeded, so two builds can be
+    compared output for output.
 Extra legs, reported in the same line: batch-256 throughput, host-API p50 latency, the 1M-row
 configuration, roofline of the dominant kernel (HIP events recorded by the library around the scan
 kernel on its launch stream), and a CPU baseline (oracle, bounded sample) on rank 0 at N=1.
@@ -36,6 +39,7 @@ I6_MIN_ROWS = 3 << 18  # indexes of at least this many rows answer single querie
 
 MAX_LINE_BYTES = 8192  # the driver keeps the last 8 KB of stdout: the result line must fit (round-4 verdict: a 20 KB line was lost)
 EXTRA_FILE = os.path.join(ROOT, "bench_extra.json")  # every leg in full; the result line carries the headline scalars only
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all .npy files of one dump together
 
 
 def _get(d, *path):
@@ -154,7 +158,34 @@ def parse():
                     help="N > 1: skip the single-process leg (tools/sharded_capi_bench.py: one process, N GPUs, C ABI only)")
     ap.add_argument("--force-collective", action="store_true",
                     help="run the all-gather + packed merge even at world size 1 (exercises the N>1 code path)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps of the headline leg, write what its last step returned (labels, distances, "
+                         "found) as DIR/<name>.npy, for comparing two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(dirpath: str, arrays: dict) -> dict:
+    """--dump-outputs: `arrays` (each [B, ...], one row per query) as dirpath/<name>.npy, integers as float64 (exact below
+    2**53: labels are row ids), floats as float32.  Past DUMP_MAX_BYTES in all, the same seeded sample of rows is kept from
+    every array and its row numbers are written as rows.npy.  Returns {file name: shape}."""
+    os.makedirs(dirpath, exist_ok=True)
+    conv = {n: np.ascontiguousarray(a, dtype=np.float64 if a.dtype.kind in "iub" or a.dtype == np.float64 else np.float32)
+            for n, a in arrays.items()}
+    n_rows = len(next(iter(conv.values())))
+    assert all(len(a) == n_rows for a in conv.values()), {n: a.shape for n, a in conv.items()}
+    total = sum(a.nbytes for a in conv.values())
+    if total + 4096 > DUMP_MAX_BYTES:  # (4 KiB: the .npy headers)
+        per_row = total // max(n_rows, 1) + 8  # (+ its entry in rows.npy)
+        keep = max(1, min(n_rows, (DUMP_MAX_BYTES - 4096) // per_row))
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, keep, replace=False))
+        conv = {n: a[rows] for n, a in conv.items()}
+        conv["rows"] = rows.astype(np.float64)
+    for n, a in conv.items():
+        np.save(os.path.join(dirpath, n + ".npy"), a)
+    return {n + ".npy": list(a.shape) for n, a in conv.items()}
 
 
 def cpu_baseline(sample_rows: int, k: int, total_rows: int):
@@ -428,12 +459,14 @@ def main():
                 merge(j)
 
         def result():
+            """labels [Bq, k] int64, distances [Bq, k] f32, found [Bq] u32 of the last step"""
             drain()
             torch.cuda.synchronize()
             if collective:
-                return o_lab.cpu().numpy(), o_dist.cpu().numpy()
+                return o_lab.cpu().numpy(), o_dist.cpu().numpy(), o_found.cpu().numpy()
             raw = blobs[0].cpu().numpy()
-            return (raw[:off_d].view(np.int64).reshape(Bq, k), raw[off_d:off_f].view(np.float32).reshape(Bq, k))
+            return (raw[:off_d].view(np.int64).reshape(Bq, k), raw[off_d:off_f].view(np.float32).reshape(Bq, k),
+                    raw[off_f:off_f + Bq * 4].view(np.uint32).copy())
 
         step.drain = drain
         return step, result
@@ -458,9 +491,10 @@ def main():
             return -(-Bq // 256)          # matrix-core path: 256 queries per pass (scan_batched.hip)
         return -(-Bq // 8)                # streaming path over 16-bit fragments: 8 queries per pass
 
-    def run_leg(index, Bq, steps, warmup, seed=2, check_planted=False, rows_read="default"):
+    def run_leg(index, Bq, steps, warmup, seed=2, check_planted=False, rows_read="default", dump_dir=None):
         """`steps` timed searches of a Bq-query batch.  Returns qps (max over ranks), ms/step and the mean
-        duration of the dominant scan kernel measured with HIP events on its launch stream."""
+        duration of the dominant scan kernel measured with HIP events on its launch stream.  dump_dir: rank 0 writes the
+        last timed step's results there (dump_outputs)."""
         step, result = make_step(index, Bq, seed)
         f6_before = index.stats_batch_feedback()["f6_batches"] if Bq >= 2 else 0
         index.profile_enable(True)
@@ -513,8 +547,11 @@ def main():
                     leg["mfma_frac_i8_dense_peak"] = leg["mfma_TFLOPs"] / 5000.0
                 else:
                     leg["mfma_frac_f16_dense_peak"] = leg["mfma_TFLOPs"] / 2500.0
+        if dump_dir is not None and rank == 0:
+            labels, dists, found = result()
+            leg["outputs_dumped"] = dump_outputs(dump_dir, {"labels": labels, "distances": dists, "found": found})
         if check_planted:
-            labels, _ = result()
+            labels, _, _ = result()
             leg["planted_top1_ok"] = bool(labels[0][0] == 1 + (4242 % args.rows))
             leg["planted_labels"] = [int(v) for v in labels[0]]
         return leg, algo
@@ -757,7 +794,7 @@ def main():
         return res
 
     # ---- headline leg ------------------------------------------------------------------------
-    head, algo_bytes = run_leg(idx, B, args.steps, args.warmup, check_planted=True)
+    head, algo_bytes = run_leg(idx, B, args.steps, args.warmup, check_planted=True, dump_dir=args.dump_outputs)
     qps = head["queries_per_s"]
     elapsed_ms = head["ms_per_step"]
     scan_avg_ms = head["scan_kernel_ms"]

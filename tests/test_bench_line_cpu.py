@@ -7,6 +7,8 @@ import os
 import sys
 from contextlib import redirect_stdout
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -61,3 +63,48 @@ def test_an_oversized_line_is_refused():
         assert "result line" in str(e)
     else:
         raise AssertionError("an oversized line went through")
+
+
+def test_dump_outputs_writes_float_arrays_the_caller_receives(tmp_path):
+    rng = np.random.default_rng(1)
+    labels = rng.integers(1, 100_000_001, size=(3, 10), dtype=np.int64)
+    dists = rng.random((3, 10), dtype=np.float32)
+    found = np.array([10, 10, 7], np.uint32)
+    shapes = bench.dump_outputs(str(tmp_path), {"labels": labels, "distances": dists, "found": found})
+    assert shapes == {"labels.npy": [3, 10], "distances.npy": [3, 10], "found.npy": [3]}
+    lab, dis, fnd = (np.load(tmp_path / n) for n in ("labels.npy", "distances.npy", "found.npy"))
+    assert lab.dtype == np.float64 and np.array_equal(lab.astype(np.int64), labels)
+    assert dis.dtype == np.float32 and np.array_equal(dis.view(np.uint32), dists.view(np.uint32))
+    assert fnd.dtype == np.float64 and np.array_equal(fnd, found)
+    assert not (tmp_path / "rows.npy").exists()
+
+
+def test_dump_outputs_samples_the_same_rows_of_a_large_output_within_64_mb(tmp_path):
+    B, k = 1 << 16, 100  # 65536 x 100 labels (f64) + distances (f32): 75 MiB before sampling
+    labels = np.arange(B * k, dtype=np.int64).reshape(B, k)
+    dists = (labels % 1000).astype(np.float32)
+    runs = []
+    for sub in ("a", "b"):
+        d = tmp_path / sub
+        bench.dump_outputs(str(d), {"labels": labels, "distances": dists})
+        assert sum(f.stat().st_size for f in d.iterdir()) <= bench.DUMP_MAX_BYTES == 64 << 20
+        runs.append({n: np.load(d / (n + ".npy")) for n in ("labels", "distances", "rows")})
+    rows = runs[0]["rows"].astype(np.int64)
+    assert 0 < len(rows) < B and np.all(np.diff(rows) > 0)
+    assert np.array_equal(runs[0]["labels"].astype(np.int64), labels[rows])
+    assert np.array_equal(runs[0]["distances"], dists[rows])
+    for n in runs[0]:
+        assert np.array_equal(runs[0][n], runs[1][n])
+
+
+def test_steps_below_one_are_refused(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    try:
+        bench.parse()
+    except SystemExit as e:
+        assert e.code == 2
+    else:
+        raise AssertionError("--steps 0 was accepted")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "0", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.steps == 7 and args.warmup == 0 and args.dump_outputs == "d"

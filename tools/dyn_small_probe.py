@@ -1,7 +1,7 @@
 """Static interleave against the dynamically assigned tail of the packed stream on small indexes (dev tool).  python tools/dyn_small_probe.py"""
 import os, sys, time
 import torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import dawnsearch_amd as dawn
 from dawnsearch_amd import synth
 dev = torch.device("cuda", 0); stream = torch.cuda.current_stream().cuda_stream
