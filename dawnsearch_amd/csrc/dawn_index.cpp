@@ -889,6 +889,73 @@ int index_clear(dawn_index* idx) {
     return DAWN_OK;
 }
 
+// Removal by label (dawn_index_remove; kernels: index_compact.hip).  The rows, their labels and every shadow end up exactly as
+// if the surviving rows had been added in their original order: the rows move in place, the shadows are re-quantised from the
+// sub-tile of the first removed row on (whole 32-row sub-tiles, as after an add), and the feedback starts over as after a load.
+int index_remove_single(dawn_index* idx, size_t n_ids, const uint64_t* ids, size_t* removed) {
+    if (removed) *removed = 0;
+    if (n_ids == 0 || idx->size == 0) return DAWN_OK;
+    DAWN_TRY(set_device(idx));
+    std::vector<uint64_t> rm(ids, ids + n_ids);
+    std::sort(rm.begin(), rm.end());
+    rm.erase(std::unique(rm.begin(), rm.end()), rm.end());
+    const uint32_t n = (uint32_t)idx->size;
+    const uint32_t n_chunks = (n + CMP_CHUNK - 1) / CMP_CHUNK, nb = compact_blocks(n);
+    // device workspace: [4] control words {first removed, claim, -, -} | mask [n_chunks] | prefixes [n_chunks] | blocks [nb + 1] |
+    // the removed labels (0.25 B per row + the list: the only memory the removal takes)
+    const size_t words = 4 + 2 * (size_t)n_chunks + nb + 1;
+    const size_t bytes = (words * sizeof(uint32_t) + 7) / 8 * 8 + rm.size() * sizeof(uint64_t);
+    char* ws = nullptr;
+    DAWN_HIP_TRY(hipMalloc((void**)&ws, bytes));
+    struct Free {
+        char* p;
+        ~Free() { (void)hipFree(p); }
+    } free_ws{ws};
+    uint32_t* d_ctl = reinterpret_cast<uint32_t*>(ws);
+    uint32_t* d_mask = d_ctl + 4;
+    uint32_t* d_pre = d_mask + n_chunks;
+    uint32_t* d_blk = d_pre + n_chunks;
+    uint64_t* d_rm = reinterpret_cast<uint64_t*>(ws + (words * sizeof(uint32_t) + 7) / 8 * 8);
+    hipStream_t st = idx->stream;
+    DAWN_HIP_TRY(hipMemcpyAsync(d_rm, rm.data(), rm.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    DAWN_HIP_TRY(hipMemsetAsync(d_ctl, 0xFF, sizeof(uint32_t), st));  // first removed: none yet
+    launch_compact_mark(idx->d_ids, n, d_rm, (uint32_t)rm.size(), d_mask, d_pre, d_blk, d_ctl, d_ctl + 1, st);
+    uint32_t* h = reinterpret_cast<uint32_t*>(idx->h_pinned);
+    DAWN_HIP_TRY(hipMemcpyAsync(h, d_ctl, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DAWN_HIP_TRY(hipMemcpyAsync(h + 1, d_blk + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    DAWN_HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t first = h[0], kept = h[1];
+    if (kept == n) return DAWN_OK;  // no label matched: nothing changes
+    if (first >= n || kept > n) return fail(DAWN_ERR_HIP, "removal: inconsistent counts (%u kept of %u, first %u)", kept, n, first);
+    // from here on a device failure leaves the index empty (the rows may be half moved)
+    auto lose = [&](int rc) {
+        (void)hipGetLastError();
+        (void)index_clear(idx);
+        return rc;
+    };
+    launch_compact_move(idx->d_x, idx->dtype == DAWN_DTYPE_BF16 ? ROW_BF16 : ROW_F32, idx->d_ids, d_mask, d_pre, d_blk, d_ctl + 1, n,
+                        first, idx->mfma_blocks * 4, st);
+    if (hipGetLastError() != hipSuccess) return lose(fail(DAWN_ERR_HIP, "removal: launch failed"));
+    // the vacated rows go back to zeros as in a grown allocation (a bf16 index keeps them: rows >= size are masked by position)
+    if (idx->dtype != DAWN_DTYPE_BF16 && hipMemsetAsync(idx->d_x + (size_t)kept * idx->row_bytes(), 0, (size_t)(n - kept) * idx->row_bytes(), st) != hipSuccess)
+        return lose(fail(DAWN_ERR_HIP, "removal: hipMemsetAsync failed"));
+    if (hipStreamSynchronize(st) != hipSuccess) return lose(fail(DAWN_ERR_HIP, "removal: the move failed"));
+    idx->size = kept;
+    // every shadow's converted prefix goes back to the sub-tile of the first removed row (the f16 shadow converts whole 64-row
+    // tiles from there): index_prepare_search re-quantises from that point
+    const size_t keep_rows = (size_t)first / 32 * 32;
+    idx->shadow_rows = std::min(idx->shadow_rows, keep_rows);
+    idx->i8_rows = std::min(idx->i8_rows, keep_rows);
+    idx->i6_rows = std::min(idx->i6_rows, keep_rows);
+    idx->f6_rows = std::min(idx->f6_rows, keep_rows);
+    idx->i6_slack_dirty = true;
+    int rc = index_prepare_search(idx, /*appended=*/false);  // (the contents changed: the feedback starts over)
+    if (rc == DAWN_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(DAWN_ERR_HIP, "removal: shadow update failed");
+    if (rc != DAWN_OK) return lose(rc);
+    if (removed) *removed = n - kept;
+    return DAWN_OK;
+}
+
 // Synthetic unit rows appended as pending rows: rows first_row.. of stream `seed`; labels first_id + i, or
 // (a shard of a sharded index) the global positions first_pos + i.
 int index_fill_async(dawn_index* idx, uint64_t seed, uint64_t first_row, size_t n, uint64_t first_id, bool ids_are_positions,
@@ -1501,6 +1568,17 @@ int dawn_index_add(dawn_index* idx, uint64_t id, const float* v) {
         idx->h_add_ids[idx->staged] = id;
         ++idx->staged;
         return DAWN_OK;
+    });
+}
+
+int dawn_index_remove(dawn_index* idx, size_t n, const uint64_t* ids, size_t* removed) {
+    if (removed) *removed = 0;
+    if (!idx || (!ids && n)) return fail(DAWN_ERR_INVALID_ARG, "NULL argument");
+    if (idx->shards) return fail(DAWN_ERR_UNSUPPORTED, "remove: not supported on a sharded index (chunk dealing maps positions to shards)");
+    if (n == 0) return DAWN_OK;
+    return dawn::guarded([&] {
+        DAWN_TRY(flush_adds(idx));  // (a staged row can be removed)
+        return dawn::index_remove_single(idx, n, ids, removed);
     });
 }
 

@@ -306,6 +306,8 @@ int index_append_finish(dawn_index* idx, bool keep);     // make the pending row
 int index_append_commit(dawn_index* idx);   // check + finish: DAWN_OK / DAWN_ERR_NOT_NORMALIZED (nothing added) / error
 void index_append_abort(dawn_index* idx);   // drop the pending rows (I/O error half way)
 int index_clear(dawn_index* idx);           // size = 0 (load replaces the contents)
+// rows whose label is one of ids[0..n_ids) leave the index (compacted in place); *removed (may be NULL) = rows removed
+int index_remove_single(dawn_index* idx, size_t n_ids, const uint64_t* ids, size_t* removed);
 int index_fill_async(dawn_index* idx, uint64_t seed, uint64_t first_row, size_t n, uint64_t first_id, bool ids_are_positions,
                      uint64_t first_pos);
 // Workspaces + filter shadows for the current rows and options, on idx->stream (callers synchronise).

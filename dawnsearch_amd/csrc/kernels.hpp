@@ -284,6 +284,17 @@ void launch_validate_rows(const float* d_rows, uint32_t n, uint32_t* d_bad_count
 void launch_fill_synth(uint64_t seed, uint64_t first_row, uint32_t n, float* d_out, float* d_len, int dist,
                        hipStream_t stream);
 void launch_iota_u64(uint64_t* d_out, uint64_t first, uint32_t n, hipStream_t stream);
+// Removal by label (index_compact.hip).  mark + scan: keep mask [ceil(n / 32)], per-chunk prefix of kept rows inside its
+// block [ceil(n / 32)], block totals -> exclusive offsets [compact_blocks(n) + 1] (the last: rows kept), *d_first_removed =
+// min(itself, first removed row) (the caller sets it to ~0u), *d_claim = 0.  move: in place and stable, from the chunk of
+// first_row (<= the first removed row) on; d_pre is consumed.  grid: resident workgroups (chunks are claimed from d_claim).
+constexpr uint32_t CMP_CHUNK = 32;          // rows per chunk of the move (one keep-mask word)
+constexpr uint32_t CMP_BLOCK_CHUNKS = 256;  // chunks per workgroup of the mark pass
+inline uint32_t compact_blocks(uint32_t n_rows) { return (n_rows + CMP_CHUNK * CMP_BLOCK_CHUNKS - 1) / (CMP_CHUNK * CMP_BLOCK_CHUNKS); }
+void launch_compact_mark(const uint64_t* d_ids, uint32_t n_rows, const uint64_t* d_rm, uint32_t n_rm, uint32_t* d_mask, uint32_t* d_pre,
+                         uint32_t* d_blk, uint32_t* d_first_removed, uint32_t* d_claim, hipStream_t stream);
+void launch_compact_move(void* d_x, int rt, uint64_t* d_ids, const uint32_t* d_mask, uint32_t* d_pre, const uint32_t* d_blk,
+                         uint32_t* d_claim, uint32_t n_rows, uint32_t first_row, int grid, hipStream_t stream);
 // bf16 index rows <-> f32 rows: d_in[n][384] f32 -> rows first_row.. of the fragment-ordered index d_x (round to nearest
 // even), and back (exact widening).
 void launch_rows_f32_to_bf16(const float* d_in, void* d_x, size_t first_row, size_t n_rows, hipStream_t stream);

@@ -68,6 +68,14 @@ class VectorIndex:
         assert rows.ndim == 2 and rows.shape[1] == EM_LEN and ids.shape == (rows.shape[0],)
         check(lib.dawn_index_add_batch(self._h, rows.shape[0], _ptr(ids), _ptr(rows)))
 
+    def remove(self, ids) -> int:
+        """Index::remove: every row labelled with one of `ids` (an int or an array of them) leaves the index, which is then
+        the index of the surviving rows added in their order (dawn_index_remove).  -> rows removed."""
+        ids = np.ascontiguousarray(np.atleast_1d(np.asarray(ids, dtype=np.uint64)).ravel())
+        removed = C.c_size_t(0)
+        check(lib.dawn_index_remove(self._h, ids.shape[0], _ptr(ids), C.byref(removed)))
+        return removed.value
+
     def search(self, q: np.ndarray, count: int):
         """-> (labels u64[found], distances f32[found]) ascending by distance."""
         q = np.ascontiguousarray(q, dtype=np.float32)

@@ -131,6 +131,21 @@ class SearchProvider:
             self._by_url[pages[i].url] = id_
         self._next_rowid += len(keep)
 
+    def remove_pages(self, ids) -> int:
+        """Drop pages (an id or ids) from the store and the index: their rows leave the index (dawn_index_remove), the
+        space they held counts again for `insert`, and a later `insert` of the same URL indexes it under a new rowid
+        (the re-crawl case).  Ids not stored are ignored.  -> pages removed."""
+        ids = [int(i) for i in np.atleast_1d(np.asarray(ids, dtype=np.uint64))]
+        gone = sorted({i for i in ids if i in self._pages})
+        if not gone:
+            return 0
+        self.index.remove(np.asarray(gone, dtype=np.uint64))
+        for id_ in gone:
+            url = self._pages.pop(id_)[0]
+            if self._by_url.get(url) == id_:
+                del self._by_url[url]
+        return len(gone)
+
     # -- :127-153 ---------------------------------------------------------------------------------
     def fill_index_from_db(self) -> None:
         count = self.page_count()

@@ -91,6 +91,15 @@ int dawn_index_add(dawn_index *idx, uint64_t id, const float *v);
 /* Bulk form of fill_index_from_db's loop (:135-150): n rows in one transfer + one validation kernel.
  * On a non-normalised row nothing is added and DAWN_ERR_NOT_NORMALIZED is returned. */
 int dawn_index_add_batch(dawn_index *idx, size_t n, const uint64_t *ids, const float *v);
+/* Removes every row whose label is one of ids[0..n) (usearch Index::remove for a batch of keys).  *removed = rows removed
+ * (NULL = not wanted); ids that match no row are not an error, an id given twice counts once, a label held by several
+ * rows removes all of them.  Afterwards the index is identical — rows, labels, their order, every filter shadow, search
+ * results, save files — to one built by adding the surviving rows in their original order; capacity() is unchanged.
+ * Staged adds are applied first (a staged row can be removed).  Cost: one in-place pass over the rows from the first
+ * removed position to the end, plus re-quantising the shadows' sub-tiles from there; removing rows near the end is cheap.
+ * A captured hipGraph of dawn_index_search_device must be re-captured (as after add).  Sharded handles:
+ * DAWN_ERR_UNSUPPORTED, nothing changed.  A device error part way leaves the index EMPTY (as a failed load does). */
+int dawn_index_remove(dawn_index *idx, size_t n, const uint64_t *ids, size_t *removed);
 
 /* index.search(query, count) -> Matches{labels, distances} :214.  Exact: distances[i] =
  * 1.0f - (sequential f32 sum of q_i*x_i) bit-for-bit as vector.rs:128-134, ascending, ties ->
