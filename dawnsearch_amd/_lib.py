@@ -66,6 +66,9 @@ _SIGS = {
     "dawn_index_add": (_i32, [_vp, _u64, _vp]),
     "dawn_index_add_batch": (_i32, [_vp, _sz, _vp, _vp]),
     "dawn_index_remove": (_i32, [_vp, _sz, _vp, C.POINTER(_sz)]),
+    "dawn_index_get": (_i32, [_vp, _sz, _vp, _vp, _vp]),
+    "dawn_index_search_like": (_i32, [_vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "dawn_index_search_like_device": (_i32, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "dawn_index_search": (_i32, [_vp, _vp, _sz, _vp, _vp, C.POINTER(_sz)]),
     "dawn_index_search_batch": (_i32, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "dawn_index_search_limited": (_i32, [_vp, _vp, _sz, C.c_float, _vp, _vp, _vp]),

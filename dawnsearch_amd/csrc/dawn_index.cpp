@@ -114,6 +114,11 @@ int ensure_workspace(dawn_index* idx, size_t B) {
         DAWN_HIP_TRY(hipMalloc((void**)&idx->bounded.wide_cnt, dawn::BATCH_QT * sizeof(uint32_t)));
         DAWN_HIP_TRY(hipMemset(idx->bounded.wide_cnt, 0, dawn::BATCH_QT * sizeof(uint32_t)));
     }
+    if (!idx->d_lk) {  // rows by label (index_lookup.hip): a search_like of up to LK_PROBES labels is launches only
+        DAWN_HIP_TRY(hipMalloc((void**)&idx->d_lk, 2 * dawn::LK_PROBES * sizeof(uint64_t)));
+        DAWN_HIP_TRY(hipMalloc((void**)&idx->d_lq, (size_t)dawn::LK_PROBES * dawn::EM * sizeof(float)));
+        DAWN_HIP_TRY(hipMalloc((void**)&idx->d_lmiss, dawn::LK_PROBES * sizeof(uint32_t)));
+    }
     if (!idx->d_i6_pool) {  // chunk counters of the packed stream: zero between searches (merge_exact_kernel resets them)
         DAWN_HIP_TRY(hipMalloc((void**)&idx->d_i6_pool, 32 * sizeof(uint32_t)));
         DAWN_HIP_TRY(hipMemset(idx->d_i6_pool, 0, 32 * sizeof(uint32_t)));
@@ -748,7 +753,7 @@ void index_destroy_single(dawn_index* idx) {
         if (ev) (void)hipEventDestroy(ev);
     void* ptrs[] = {idx->d_x, idx->d_shadow, idx->d_i8, idx->d_i8meta, idx->d_i6, idx->d_i6meta, idx->d_cand_es, idx->d_cand_ep, idx->d_cand_tb, idx->d_i6_pool, idx->d_i6hist, idx->d_stage, idx->d_ids, idx->d_cand_s, idx->d_cand_p,
                     idx->d_flags, idx->d_stats, idx->bounded.wide_res, idx->bounded.wide_cnt, idx->bws.qh, idx->bws.tau, idx->bws.cnt, idx->bws.cand, idx->bws.diag, idx->bws.pool, idx->d_q,
-                    idx->d_labels, idx->d_dist, idx->d_found, idx->d_bad};
+                    idx->d_labels, idx->d_dist, idx->d_found, idx->d_bad, idx->d_lk, idx->d_lq, idx->d_lmiss};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (idx->h_pinned) (void)hipHostFree(idx->h_pinned);
@@ -1009,6 +1014,57 @@ int index_get_rows_single(dawn_index* idx, size_t first, size_t n, float* out_ro
         DAWN_HIP_TRY(hipMemcpy(out_rows, idx->d_x + first * rb, n * rb, hipMemcpyDeviceToHost));
     }
     if (out_ids) DAWN_HIP_TRY(hipMemcpy(out_ids, idx->d_ids + first, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return DAWN_OK;
+}
+
+// Rows by label (index_lookup.hip): one read of the labels per LK_PROBES requested labels.
+int index_label_lookup(dawn_index* ws, const uint64_t* d_labels, size_t n, const uint64_t* d_probes, size_t m, hipStream_t stream) {
+    // (8 workgroups per CU: each sorts the probes once, then streams its share of the labels)
+    DAWN_HIP_TRY(launch_label_lookup(d_labels, n, d_probes, (uint32_t)m, ws->d_lk, ws->d_lk + LK_PROBES, ws->mfma_blocks * 8, stream));
+    return DAWN_OK;
+}
+
+int index_get_by_label_single(dawn_index* idx, size_t n, const uint64_t* ids, float* out, size_t* counts) {
+    DAWN_TRY(set_device(idx));
+    hipStream_t st = idx->stream;
+    uint64_t* d_probes = reinterpret_cast<uint64_t*>(idx->d_q);  // (the host API's query staging)
+    uint64_t* hp = reinterpret_cast<uint64_t*>(idx->h_pinned);   // probes [LK_PROBES] | counts [LK_PROBES]
+    uint32_t slot[LK_PROBES];
+    for (size_t o = 0; o < n; o += LK_PROBES) {
+        const size_t m = std::min<size_t>(LK_PROBES, n - o);
+        std::memcpy(hp, ids + o, m * sizeof(uint64_t));
+        DAWN_HIP_TRY(hipMemcpyAsync(d_probes, hp, m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        DAWN_TRY(index_label_lookup(idx, idx->d_ids, idx->size, d_probes, m, st));
+        if (out) {
+            launch_label_gather(idx->d_x, idx->size, idx->dtype == DAWN_DTYPE_BF16 ? ROW_BF16 : ROW_F32, d_probes, (uint32_t)m, idx->d_lk,
+                                idx->d_lk + LK_PROBES, idx->d_lq, nullptr, false, st);
+            DAWN_HIP_TRY(hipGetLastError());
+            DAWN_HIP_TRY(hipMemcpyAsync(out + o * EM, idx->d_lq, m * EM * sizeof(float), hipMemcpyDeviceToHost, st));
+        }
+        if (counts)
+            DAWN_HIP_TRY(hipMemcpyAsync(hp + LK_PROBES, idx->d_lk + LK_PROBES, m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        DAWN_HIP_TRY(hipStreamSynchronize(st));
+        if (counts) {
+            label_slots(ids + o, m, slot);
+            for (size_t b = 0; b < m; ++b) counts[o + b] = (size_t)hp[LK_PROBES + slot[b]];
+        }
+    }
+    return DAWN_OK;
+}
+
+// MoreLikeSearch on the device: per LK_PROBES labels lookup -> gather (missing: e_0, a valid query) -> the search -> fixup.
+int index_search_like_on_device(dawn_index* idx, const uint64_t* d_ids, size_t B, size_t k, uint64_t* d_labels, float* d_dist,
+                                uint32_t* d_found, hipStream_t stream) {
+    const int rt = idx->dtype == DAWN_DTYPE_BF16 ? ROW_BF16 : ROW_F32;
+    for (size_t b0 = 0; b0 < B; b0 += LK_PROBES) {
+        const size_t nb = std::min<size_t>(LK_PROBES, B - b0);
+        DAWN_TRY(index_label_lookup(idx, idx->d_ids, idx->size, d_ids + b0, nb, stream));
+        launch_label_gather(idx->d_x, idx->size, rt, d_ids + b0, (uint32_t)nb, idx->d_lk, idx->d_lk + LK_PROBES, idx->d_lq, idx->d_lmiss, true,
+                            stream);
+        DAWN_TRY(index_search_on_device(idx, idx->d_lq, nb, k, d_labels + b0 * k, d_dist + b0 * k, d_found + b0, stream));
+        launch_label_fixup(idx->d_lmiss, (uint32_t)nb, d_found + b0, stream);
+    }
+    DAWN_HIP_TRY(hipGetLastError());
     return DAWN_OK;
 }
 
@@ -1639,6 +1695,69 @@ int dawn_index_search_batch(dawn_index* idx, const float* queries, size_t B, siz
         for (size_t b = 0; b < nb; ++b) found[b0 + b] = hf[b];
     }
     return DAWN_OK;
+}
+
+int dawn_index_get(dawn_index* idx, size_t n, const uint64_t* ids, float* out, size_t* counts) {
+    if (!idx || !ids) return fail(DAWN_ERR_INVALID_ARG, "NULL argument");
+    if (n == 0) return DAWN_OK;
+    return dawn::guarded([&] {
+        DAWN_TRY(flush_adds(idx));  // (a staged row can be looked up)
+        return idx->shards ? dawn::sharded_get_by_label(idx, n, ids, out, counts) : dawn::index_get_by_label_single(idx, n, ids, out, counts);
+    });
+}
+
+// The host form of dawn_index_search_like_device: the labels travel in through the query staging, the results come back as
+// in dawn_index_search_batch (zero-copy stores into the pinned block for small batches, copies otherwise).
+int dawn_index_search_like(dawn_index* idx, size_t n, const uint64_t* ids, size_t count, uint64_t* labels, float* distances,
+                           size_t* found) {
+    if (!idx || !ids || (n && (!labels || !distances || !found))) return fail(DAWN_ERR_INVALID_ARG, "NULL argument");
+    if (count == 0 || count > DAWN_MAX_K) return fail(DAWN_ERR_UNSUPPORTED, "count must be 1..%d", DAWN_MAX_K);
+    if (n == 0) return DAWN_OK;
+    return dawn::guarded([&] {
+        DAWN_TRY(flush_adds(idx));
+        if (idx->shards) return dawn::sharded_search_like(idx, n, ids, count, labels, distances, found);
+        DAWN_TRY(set_device(idx));
+        using dawn::kMaxBatch;
+        uint64_t* d_ids = reinterpret_cast<uint64_t*>(idx->d_q);
+        for (size_t b0 = 0; b0 < n; b0 += kMaxBatch) {
+            const size_t nb = std::min(kMaxBatch, n - b0);
+            char* hp = (char*)idx->h_pinned;
+            uint64_t* hi = (uint64_t*)hp;
+            uint64_t* hl = (uint64_t*)(hp + kMaxBatch * dawn::EM * 4);
+            float* hd = (float*)(hp + kMaxBatch * (dawn::EM * 4 + DAWN_MAX_K * 8));
+            uint32_t* hf = (uint32_t*)(hp + kMaxBatch * (dawn::EM * 4 + DAWN_MAX_K * 8 + DAWN_MAX_K * 4));
+            std::memcpy(hi, ids + b0, nb * sizeof(uint64_t));
+            DAWN_HIP_TRY(hipMemcpyAsync(d_ids, hi, nb * sizeof(uint64_t), hipMemcpyHostToDevice, idx->stream));
+            idx->n_searches += nb;
+            if (nb <= idx->zero_copy_batch) {
+                DAWN_TRY(dawn::index_search_like_on_device(idx, d_ids, nb, count, hl, hd, hf, idx->stream));
+            } else {
+                DAWN_TRY(dawn::index_search_like_on_device(idx, d_ids, nb, count, idx->d_labels, idx->d_dist, idx->d_found, idx->stream));
+                DAWN_HIP_TRY(hipMemcpyAsync(hl, idx->d_labels, nb * count * sizeof(uint64_t), hipMemcpyDeviceToHost, idx->stream));
+                DAWN_HIP_TRY(hipMemcpyAsync(hd, idx->d_dist, nb * count * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
+                DAWN_HIP_TRY(hipMemcpyAsync(hf, idx->d_found, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, idx->stream));
+            }
+            DAWN_HIP_TRY(hipStreamSynchronize(idx->stream));
+            std::memcpy(labels + b0 * count, hl, nb * count * sizeof(uint64_t));
+            std::memcpy(distances + b0 * count, hd, nb * count * sizeof(float));
+            for (size_t b = 0; b < nb; ++b) found[b0 + b] = hf[b];
+        }
+        return DAWN_OK;
+    });
+}
+
+int dawn_index_search_like_device(dawn_index* idx, const uint64_t* d_ids, size_t B, size_t count, uint64_t* d_labels,
+                                  float* d_distances, uint32_t* d_found, void* stream) {
+    if (!idx || !d_ids || !d_labels || !d_distances || !d_found) return fail(DAWN_ERR_INVALID_ARG, "NULL argument");
+    if (count == 0 || count > DAWN_MAX_K) return fail(DAWN_ERR_UNSUPPORTED, "count must be 1..%d", DAWN_MAX_K);
+    if (idx->shards) return fail(DAWN_ERR_UNSUPPORTED, "search_like_device: not supported on a sharded index (rows live on the peers)");
+    if (B == 0) return DAWN_OK;
+    return dawn::guarded([&] {
+        DAWN_TRY(flush_adds(idx));  // (staged rows join the index: this one call synchronises, as dawn_index_search_device)
+        DAWN_TRY(set_device(idx));
+        idx->n_searches += B;
+        return dawn::index_search_like_on_device(idx, d_ids, B, count, d_labels, d_distances, d_found, (hipStream_t)stream);
+    });
 }
 
 int dawn_index_search(dawn_index* idx, const float* query, size_t count, uint64_t* labels, float* distances,

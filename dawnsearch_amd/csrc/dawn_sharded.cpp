@@ -485,6 +485,55 @@ int sharded_get_rows(dawn_index* idx, size_t first, size_t n, float* out_rows, u
     return DAWN_OK;
 }
 
+// Rows by label: the lookup runs on the root over the global labels in insertion order (S.d_gids), its first positions are
+// mapped to (shard, local row) and read from there.
+int sharded_get_by_label(dawn_index* idx, size_t n, const uint64_t* ids, float* out, size_t* counts) {
+    ShardSet& S = *idx->shards;
+    dawn_index* r = S.sh[0];  // the root shard's workspace and staging
+    uint64_t* d_probes = reinterpret_cast<uint64_t*>(r->d_q);
+    uint64_t* hp = reinterpret_cast<uint64_t*>(r->h_pinned);  // probes [LK_PROBES] | first [LK_PROBES] | count [LK_PROBES]
+    uint32_t slot[LK_PROBES];
+    for (size_t o = 0; o < n; o += LK_PROBES) {
+        const size_t m = std::min<size_t>(LK_PROBES, n - o);
+        DAWN_HIP_TRY(hipSetDevice(root_dev(S)));
+        std::memcpy(hp, ids + o, m * sizeof(uint64_t));
+        DAWN_HIP_TRY(hipMemcpyAsync(d_probes, hp, m * sizeof(uint64_t), hipMemcpyHostToDevice, r->stream));
+        DAWN_TRY(index_label_lookup(r, S.d_gids, S.size, d_probes, m, r->stream));
+        DAWN_HIP_TRY(hipMemcpyAsync(hp + LK_PROBES, r->d_lk, 2 * LK_PROBES * sizeof(uint64_t), hipMemcpyDeviceToHost, r->stream));
+        DAWN_HIP_TRY(hipStreamSynchronize(r->stream));
+        label_slots(ids + o, m, slot);
+        for (size_t b = 0; b < m; ++b) {
+            const uint64_t c = hp[2 * LK_PROBES + slot[b]], p = hp[LK_PROBES + slot[b]];
+            if (counts) counts[o + b] = (size_t)c;
+            if (!out) continue;
+            float* row = out + (o + b) * EM;
+            if (c == 0) {
+                std::memset(row, 0, EM * sizeof(float));
+                continue;
+            }
+            if (p >= S.size) return fail(DAWN_ERR_HIP, "get: lookup returned position %llu of %zu", (unsigned long long)p, S.size);
+            int s;
+            size_t local;
+            S.locate((size_t)p, &s, &local);
+            DAWN_TRY(index_get_rows_single(S.sh[s], local, 1, row, nullptr));
+        }
+    }
+    return DAWN_OK;
+}
+
+int sharded_search_like(dawn_index* idx, size_t n, const uint64_t* ids, size_t count, uint64_t* labels, float* distances,
+                        size_t* found) {
+    std::vector<float> q(n * EM);
+    std::vector<size_t> c(n);
+    DAWN_TRY(sharded_get_by_label(idx, n, ids, q.data(), c.data()));
+    for (size_t b = 0; b < n; ++b)
+        if (c[b] == 0) q[b * EM] = 1.0f;  // (a missing label searches e_0, a valid query, and reports nothing)
+    DAWN_TRY(sharded_search_batch(idx, q.data(), n, count, labels, distances, found));
+    for (size_t b = 0; b < n; ++b)
+        if (c[b] == 0) found[b] = 0;
+    return DAWN_OK;
+}
+
 int sharded_set_option(dawn_index* idx, const char* name, int64_t value) {
     ShardSet& S = *idx->shards;
     const std::string n(name);

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <exception>
 #include <new>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -189,6 +190,11 @@ struct dawn_index {
     uint32_t* d_found = nullptr;
     uint32_t* d_bad = nullptr;
     void* h_pinned = nullptr;  // kMaxBatch * (384*4 + 64*8 + 64*4 + 4 + 4)
+    // rows by label (index_lookup.hip; allocated with the search workspaces): the lookup's slots first [LK_PROBES] | count
+    // [LK_PROBES] (u64), the gathered rows / queries [LK_PROBES][384] f32 and their "missing" flags [LK_PROBES]
+    uint64_t* d_lk = nullptr;
+    float* d_lq = nullptr;
+    uint32_t* d_lmiss = nullptr;
     size_t h_pinned_bytes = 0;
 
     bool profiling = false;
@@ -314,6 +320,18 @@ int index_fill_async(dawn_index* idx, uint64_t seed, uint64_t first_row, size_t 
 int index_prepare_search(dawn_index* idx, bool appended = false);  // appended: rows were added, nothing else changed
 int index_set_option_single(dawn_index* idx, const char* name, int64_t value);
 int index_get_rows_single(dawn_index* idx, size_t first, size_t n, float* out_rows, uint64_t* out_ids);
+// Rows by label (dawn_index_get / dawn_index_search_like).  lookup: the lookup launch over d_labels[0..n) for
+// d_probes[0..m) (m <= LK_PROBES) into ws's slots, on `stream` (ws: the index whose workspace holds them).  The rest as the ABI.
+// slot[i] = the first j <= i with ids[j] == ids[i]: the lookup slot request i reads (index_lookup.hip)
+inline void label_slots(const uint64_t* ids, size_t m, uint32_t* slot) {
+    std::unordered_map<uint64_t, uint32_t> seen;
+    seen.reserve(m * 2);
+    for (size_t i = 0; i < m; ++i) slot[i] = seen.emplace(ids[i], (uint32_t)i).first->second;
+}
+int index_label_lookup(dawn_index* ws, const uint64_t* d_labels, size_t n, const uint64_t* d_probes, size_t m, hipStream_t stream);
+int index_get_by_label_single(dawn_index* idx, size_t n, const uint64_t* ids, float* out, size_t* counts);
+int index_search_like_on_device(dawn_index* idx, const uint64_t* d_ids, size_t B, size_t k, uint64_t* d_labels, float* d_dist,
+                                uint32_t* d_found, hipStream_t stream);
 int index_memory_single(dawn_index* idx, uint64_t* rows_bytes, uint64_t* shadow_bytes, uint64_t* other_bytes);
 int index_stats_single(dawn_index* idx, uint64_t* searches, uint64_t* second, uint64_t* fallbacks, uint64_t* deepened,
                        uint64_t* bounded = nullptr, uint64_t* packed_failures = nullptr, uint64_t* demoted = nullptr);
@@ -337,6 +355,9 @@ int sharded_search_batch(dawn_index* idx, const float* queries, size_t B, size_t
                          size_t* found);
 int sharded_fill_synthetic(dawn_index* idx, uint64_t seed, uint64_t first_row, size_t n, uint64_t first_id);
 int sharded_get_rows(dawn_index* idx, size_t first, size_t n, float* out_rows, uint64_t* out_ids);
+int sharded_get_by_label(dawn_index* idx, size_t n, const uint64_t* ids, float* out, size_t* counts);
+int sharded_search_like(dawn_index* idx, size_t n, const uint64_t* ids, size_t count, uint64_t* labels, float* distances,
+                        size_t* found);
 int sharded_set_option(dawn_index* idx, const char* name, int64_t value);
 int sharded_memory(dawn_index* idx, uint64_t* rows_bytes, uint64_t* shadow_bytes, uint64_t* other_bytes);
 int sharded_stats(dawn_index* idx, uint64_t* searches, uint64_t* second, uint64_t* fallbacks, uint64_t* deepened,

@@ -295,6 +295,17 @@ void launch_compact_mark(const uint64_t* d_ids, uint32_t n_rows, const uint64_t*
                          uint32_t* d_blk, uint32_t* d_first_removed, uint32_t* d_claim, hipStream_t stream);
 void launch_compact_move(void* d_x, int rt, uint64_t* d_ids, const uint32_t* d_mask, uint32_t* d_pre, const uint32_t* d_blk,
                          uint32_t* d_claim, uint32_t n_rows, uint32_t first_row, int grid, hipStream_t stream);
+// Rows by label (index_lookup.hip).  lookup: d_first[i] = lowest position p < n with d_labels[p] == d_probes[i] (~0 if none),
+// d_count[i] = how many, for i the FIRST occurrence of its label in d_probes (later occurrences' slots stay ~0 / 0); the slots
+// are reset here (by a kernel: launches only).  grid: workgroups at most.  gather: d_rows[b] = the row d_first[slot of b]
+// (< n_rows) of the index d_x as f32 ([n_probes][384]; a bf16 row widened exactly), or — count 0 — zeros (unit_fill: e_0, a valid query), and
+// d_missing[b] (NULL = not wanted).  fixup: d_found[b] = 0 where d_missing[b].
+constexpr uint32_t LK_PROBES = 256;  // probe labels per lookup launch
+hipError_t launch_label_lookup(const uint64_t* d_labels, size_t n, const uint64_t* d_probes, uint32_t n_probes, uint64_t* d_first,
+                               uint64_t* d_count, int grid, hipStream_t stream);
+void launch_label_gather(const void* d_x, size_t n_rows, int rt, const uint64_t* d_probes, uint32_t n_probes, const uint64_t* d_first,
+                         const uint64_t* d_count, float* d_rows, uint32_t* d_missing, bool unit_fill, hipStream_t stream);
+void launch_label_fixup(const uint32_t* d_missing, uint32_t B, uint32_t* d_found, hipStream_t stream);
 // bf16 index rows <-> f32 rows: d_in[n][384] f32 -> rows first_row.. of the fragment-ordered index d_x (round to nearest
 // even), and back (exact widening).
 void launch_rows_f32_to_bf16(const float* d_in, void* d_x, size_t first_row, size_t n_rows, hipStream_t stream);

@@ -76,6 +76,27 @@ class VectorIndex:
         check(lib.dawn_index_remove(self._h, ids.shape[0], _ptr(ids), C.byref(removed)))
         return removed.value
 
+    def get(self, ids):
+        """Index::get / count by label for an int or an array of them (dawn_index_get) -> (rows [n,384] f32: the row of each label —
+        the earliest-added one holding it — zeros where the label is missing; counts [n] int64: rows holding each label)."""
+        ids = np.ascontiguousarray(np.atleast_1d(np.asarray(ids, dtype=np.uint64)).ravel())
+        n = ids.shape[0]
+        rows = np.zeros((n, EM_LEN), dtype=np.float32)
+        counts = np.zeros(n, dtype=np.uintp)
+        check(lib.dawn_index_get(self._h, n, _ptr(ids), _ptr(rows), _ptr(counts)))
+        return rows, counts.astype(np.int64)
+
+    def search_like(self, ids, count: int):
+        """MoreLikeSearch (search_service.rs:105-123) for a batch of labels: query b is the row of ids[b] (dawn_index_search_like)
+        -> (labels [n,count], distances [n,count], found [n]; 0 where the label is missing)."""
+        ids = np.ascontiguousarray(np.atleast_1d(np.asarray(ids, dtype=np.uint64)).ravel())
+        n = ids.shape[0]
+        labels = np.zeros((n, count), dtype=np.uint64)
+        dist = np.zeros((n, count), dtype=np.float32)
+        found = np.zeros(n, dtype=np.uintp)
+        check(lib.dawn_index_search_like(self._h, n, _ptr(ids), count, _ptr(labels), _ptr(dist), _ptr(found)))
+        return labels, dist, found.astype(np.int64)
+
     def search(self, q: np.ndarray, count: int):
         """-> (labels u64[found], distances f32[found]) ascending by distance."""
         q = np.ascontiguousarray(q, dtype=np.float32)
@@ -118,6 +139,10 @@ class VectorIndex:
     def search_device(self, d_queries: int, B: int, count: int, d_labels: int, d_distances: int, d_found: int,
                       stream: int = 0):
         check(lib.dawn_index_search_device(self._h, d_queries, B, count, d_labels, d_distances, d_found, stream))
+
+    def search_like_device(self, d_ids: int, B: int, count: int, d_labels: int, d_distances: int, d_found: int,
+                           stream: int = 0):
+        check(lib.dawn_index_search_like_device(self._h, d_ids, B, count, d_labels, d_distances, d_found, stream))
 
     # -- bench / test utilities -----------------------------------------------------------------
     def fill_synthetic(self, seed: int, first_row: int, n: int, first_id: int = 1):

@@ -101,6 +101,22 @@ int dawn_index_add_batch(dawn_index *idx, size_t n, const uint64_t *ids, const f
  * DAWN_ERR_UNSUPPORTED, nothing changed.  A device error part way leaves the index EMPTY (as a failed load does). */
 int dawn_index_remove(dawn_index *idx, size_t n, const uint64_t *ids, size_t *removed);
 
+/* Rows by label.  Labels are not unique (dawn_index_remove treats a label held by several rows as normal).  For a label L:
+ * count(L) is the number of rows holding L; the row of L is the earliest-added row holding L — the lowest position, the row
+ * ties in search go to.  Staged single-row adds are applied first (a staged row can be looked up).  Cost: one read of the
+ * label array (8 B per row) per 256 labels requested; there is no label -> position directory.
+ *
+ * usearch Index::get / contains / count for a batch of keys.  out [n][384] (NULL = not wanted): the row of ids[b] as f32
+ * (a bf16 row is widened exactly); zeros where the label is not in the index.  counts [n] (NULL = not wanted): rows holding ids[b]
+ * (0 = not in the index).  ids may repeat and come in any order.  Sharded handles: supported. */
+int dawn_index_get(dawn_index *idx, size_t n, const uint64_t *ids, float *out, size_t *counts);
+/* MoreLikeSearch (search_service.rs:105-123) for n labels in one call: query b is the row of ids[b].  The results are
+ * bit-identical to dawn_index_search_batch on the vectors dawn_index_get returns.  A label not in the index gives found[b] = 0.
+ * There is no normalisation gate on these queries: the rows passed it when they were added.  A bf16 row can widen to a norm just
+ * outside (0.99, 1.01), and it is still searched.  count 1..DAWN_MAX_K.  Sharded handles: supported. */
+int dawn_index_search_like(dawn_index *idx, size_t n, const uint64_t *ids, size_t count,
+                           uint64_t *labels, float *distances, size_t *found);
+
 /* index.search(query, count) -> Matches{labels, distances} :214.  Exact: distances[i] =
  * 1.0f - (sequential f32 sum of q_i*x_i) bit-for-bit as vector.rs:128-134, ascending, ties ->
  * earlier-added row.  *found = min(count, size).  count <= DAWN_MAX_K.  The query must pass
@@ -146,6 +162,12 @@ int dawn_index_load_page_entries(dawn_index *idx, const char *emb_path, uint64_t
  * grows the workspaces once.) */
 int dawn_index_search_device(dawn_index *idx, const float *d_queries, size_t B, size_t count,
                              uint64_t *d_labels, float *d_distances, uint32_t *d_found, void *stream);
+/* Device-resident form of dawn_index_search_like: d_ids [B] u64 on the index's device; outputs as in dawn_index_search_device.
+ * For B <= 256 on a single-device index this is kernel launches only: no allocation and no synchronisation, so it can be captured
+ * into a hipGraph.  A replay looks the labels up again in the rows as they are; after an add or a remove the graph must be
+ * re-captured, as for dawn_index_search_device.  Sharded handles: DAWN_ERR_UNSUPPORTED. */
+int dawn_index_search_like_device(dawn_index *idx, const uint64_t *d_ids, size_t B, size_t count,
+                                  uint64_t *d_labels, float *d_distances, uint32_t *d_found, void *stream);
 /* Stable G-way merge of per-shard results (each ascending by (distance, shard-local order)) —
  * the multi-GPU counterpart of search_service.rs:214-263 (BestResults merge of local + remote).
  * d_in_labels/d_in_distances [G][B][count] (e.g. the all-gather output), d_in_found [G][B];
