@@ -66,6 +66,7 @@ _SIGS = {
     "dawn_index_add": (_i32, [_vp, _u64, _vp]),
     "dawn_index_add_batch": (_i32, [_vp, _sz, _vp, _vp]),
     "dawn_index_remove": (_i32, [_vp, _sz, _vp, C.POINTER(_sz)]),
+    "dawn_index_update": (_i32, [_vp, _sz, _vp, _vp, _vp]),
     "dawn_index_get": (_i32, [_vp, _sz, _vp, _vp, _vp]),
     "dawn_index_search_like": (_i32, [_vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "dawn_index_search_like_device": (_i32, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),

@@ -961,6 +961,157 @@ int index_remove_single(dawn_index* idx, size_t n_ids, const uint64_t* ids, size
     return DAWN_OK;
 }
 
+// ---- rows replaced in place by label (dawn_index_update; kernels: index_update.hip) ----------------------------
+// Everything lives in the index's device staging (idx->d_stage, grown once and kept): a refresh of a few hundred labels allocates
+// nothing.  The hit pass's part: keys [n] u64 | counts [n] u64 | total (a 256-B slot) | perm [n] u32 | hit positions [cap] u64 |
+// hit requests [cap] u32.  The scatter's part behind it: list counts (a 256-B slot) | dirty bits [n_words] u32 | sub-tile list
+// [max_list] u32 | tile list [max_list] u32 | vectors [chunk][384] f32.
+namespace {
+constexpr size_t kUpdateChunk = (size_t)1 << 16;  // request vectors on the device at a time (96 MiB of f32)
+
+size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+
+struct HitLayout {
+    size_t keys, cnt, total, perm, pos, req, bytes;
+    HitLayout(size_t n, size_t cap) {
+        keys = 0;
+        cnt = align256(n * 8);
+        total = cnt + align256(n * 8);
+        perm = total + 256;
+        pos = perm + align256(n * 4);
+        req = pos + align256(cap * 8);
+        bytes = req + align256(cap * 4);
+    }
+};
+
+struct ApplyLayout {
+    size_t n_words, max_list, chunk, ctl, dirty, sub, tile, vec, bytes;
+    ApplyLayout(size_t n_rows, size_t n_hits, size_t n_vec, size_t head) {
+        const size_t n_sub = (n_rows + 31) / 32;
+        n_words = (n_sub + 31) / 32;
+        max_list = std::min(n_sub, n_hits);  // (every hit dirties one sub-tile at most)
+        chunk = std::min(n_vec, kUpdateChunk);
+        ctl = align256(head);
+        dirty = ctl + 256;
+        sub = dirty + align256(n_words * 4);
+        tile = sub + align256(max_list * 4);
+        vec = tile + align256(max_list * 4);
+        bytes = vec + chunk * dawn::EM * sizeof(float);
+    }
+};
+}  // namespace
+
+// The hit pass of a request (keys sorted, no repeats; perm[j] = its place in the caller's request) over d_labels[0..n_rows), in
+// ws's staging (sized for an apply over apply_rows rows behind it as well).  cnt[j] = rows holding keys[j]; *n_hits = their sum;
+// the list stays on the device (HitLayout(n, *cap)).  Changes nothing.
+int index_update_hits(dawn_index* ws, const uint64_t* d_labels, size_t n_rows, size_t n, const uint64_t* keys, const uint32_t* perm,
+                      size_t apply_rows, uint64_t* cnt, size_t* n_hits, size_t* cap) {
+    hipStream_t st = ws->stream;
+    size_t c = std::max<size_t>(2 * n, 4096);
+    for (;;) {
+        const HitLayout H(n, c);
+        DAWN_TRY(ensure_stage(ws, ApplyLayout(apply_rows, c, n, H.bytes).bytes));
+        char* d = reinterpret_cast<char*>(ws->d_stage);
+        DAWN_HIP_TRY(hipMemcpyAsync(d + H.keys, keys, n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        DAWN_HIP_TRY(hipMemcpyAsync(d + H.perm, perm, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        DAWN_HIP_TRY(hipMemsetAsync(d + H.cnt, 0, H.perm - H.cnt, st));  // counts and total
+        // (8 workgroups per CU, as the lookup: each loads the request or its fence once, then streams its share of the labels)
+        launch_update_hits(d_labels, n_rows, reinterpret_cast<const uint64_t*>(d + H.keys), reinterpret_cast<const uint32_t*>(d + H.perm),
+                           (uint32_t)n, reinterpret_cast<uint64_t*>(d + H.cnt), reinterpret_cast<uint64_t*>(d + H.total),
+                           reinterpret_cast<uint64_t*>(d + H.pos), reinterpret_cast<uint32_t*>(d + H.req), c, ws->mfma_blocks * 8, st);
+        DAWN_HIP_TRY(hipGetLastError());
+        uint64_t* h = reinterpret_cast<uint64_t*>(ws->h_pinned);
+        DAWN_HIP_TRY(hipMemcpyAsync(h, d + H.total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        DAWN_HIP_TRY(hipMemcpyAsync(cnt, d + H.cnt, n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        DAWN_HIP_TRY(hipStreamSynchronize(st));
+        const size_t total = (size_t)h[0];
+        if (total <= c) {
+            *n_hits = total;
+            *cap = c;
+            return DAWN_OK;
+        }
+        c = total;  // labels held by several rows overflowed the list: once more, with a list of the right length
+    }
+}
+
+// Rows d_pos[0..n_hits) of idx (positions < size, all different) get the vectors of their requests, d_req[e] (NULL: e), out of
+// h_v [n_vec][384]; the listed sub-tiles of every shadow are re-quantised below its converted prefix, and the packed shadow's
+// error histogram is measured again.  The scatter's workspace sits behind `head` bytes of the staging (the caller has sized it).
+// The feedback is kept, as after an append: a refresh changes a few rows, and one that reset it would never let it learn.
+// A failure may leave rows half written: the caller empties the index.
+int index_update_apply(dawn_index* idx, const uint64_t* d_pos, const uint32_t* d_req, size_t n_hits, const float* h_v, size_t n_vec,
+                       size_t head) {
+    const ApplyLayout A(idx->size, n_hits, n_vec, head);
+    char* d = reinterpret_cast<char*>(idx->d_stage);
+    if (A.bytes > idx->stage_bytes) return fail(DAWN_ERR_HIP, "update: staging too small (%zu of %zu bytes)", idx->stage_bytes, A.bytes);
+    uint32_t* d_ctl = reinterpret_cast<uint32_t*>(d + A.ctl);
+    uint32_t* d_dirty = reinterpret_cast<uint32_t*>(d + A.dirty);
+    uint32_t* d_sub = reinterpret_cast<uint32_t*>(d + A.sub);
+    uint32_t* d_tile = reinterpret_cast<uint32_t*>(d + A.tile);
+    float* d_v = reinterpret_cast<float*>(d + A.vec);
+    hipStream_t st = idx->stream;
+    const int rt = idx->dtype == DAWN_DTYPE_BF16 ? ROW_BF16 : ROW_F32;
+    DAWN_HIP_TRY(hipMemsetAsync(d_ctl, 0, 256 + A.n_words * 4, st));  // list counts and dirty bits
+    for (size_t o = 0; o < n_vec; o += A.chunk) {
+        const size_t m = std::min(A.chunk, n_vec - o);
+        DAWN_HIP_TRY(hipMemcpyAsync(d_v, h_v + o * EM, m * EM * sizeof(float), hipMemcpyHostToDevice, st));
+        launch_update_scatter(idx->d_x, rt, idx->size, d_pos, d_req, n_hits, d_v, (uint32_t)o, (uint32_t)(o + m), d_dirty, st);
+    }
+    launch_update_dirty_list(d_dirty, (uint32_t)A.n_words, d_sub, d_tile, d_ctl, st);
+    const uint32_t ml = (uint32_t)A.max_list;
+    if (idx->d_i8 && idx->i8_rows)
+        launch_rows_to_i8s_list(idx->d_x, rt, idx->d_i8, idx->d_i8meta, d_sub, d_ctl, ml, idx->i8_rows, idx->size, st, idx->i8_levels);
+    if (idx->d_i6 && idx->i6_rows)
+        launch_rows_to_i6s_list(idx->d_x, rt, idx->i6_bits, idx->d_i6, idx->d_i6meta, d_sub, d_ctl, ml, idx->i6_rows, idx->size, st);
+    if (idx->d_f6 && idx->f6_rows)
+        launch_rows_to_f6s_list(idx->d_x, rt, idx->d_f6, idx->d_f6meta, d_sub, d_ctl, ml, idx->f6_rows, idx->size, st);
+    if (idx->d_shadow && idx->shadow_rows)
+        launch_rows_f32_to_f16s_list(reinterpret_cast<const float*>(idx->d_x), idx->d_shadow, d_tile, d_ctl + 1, ml, idx->shadow_rows,
+                                     idx->size, st);
+    DAWN_HIP_TRY(hipGetLastError());
+    idx->i6_slack_dirty = true;  // (it sizes the packed stream's lists; exactness rests on the re-written sub-tile headers)
+    DAWN_TRY(index_prepare_search(idx, /*appended=*/true));
+    DAWN_HIP_TRY(hipStreamSynchronize(st));
+    return DAWN_OK;
+}
+
+int index_update_single(dawn_index* idx, size_t n, const uint64_t* keys, const uint32_t* perm, const float* v, uint64_t* cnt) {
+    if (idx->size == 0) return DAWN_OK;
+    DAWN_TRY(set_device(idx));
+    size_t n_hits = 0, cap = 0;
+    DAWN_TRY(index_update_hits(idx, idx->d_ids, idx->size, n, keys, perm, idx->size, cnt, &n_hits, &cap));
+    if (n_hits == 0) return DAWN_OK;  // no label matched: nothing changes
+    const HitLayout H(n, cap);
+    const char* d = reinterpret_cast<const char*>(idx->d_stage);
+    const int rc = index_update_apply(idx, reinterpret_cast<const uint64_t*>(d + H.pos), reinterpret_cast<const uint32_t*>(d + H.req), n_hits,
+                                      v, n, H.bytes);
+    if (rc != DAWN_OK) {  // the rows may be half written
+        (void)hipGetLastError();
+        (void)index_clear(idx);
+    }
+    return rc;
+}
+
+// One shard's part of a sharded update: rows h_pos[e] (local positions) get h_v[e].
+int index_update_rows_single(dawn_index* idx, size_t m, const uint64_t* h_pos, const float* h_v) {
+    if (m == 0) return DAWN_OK;
+    DAWN_TRY(set_device(idx));
+    const size_t head = align256(m * sizeof(uint64_t));
+    DAWN_TRY(ensure_stage(idx, ApplyLayout(idx->size, m, m, head).bytes));
+    DAWN_HIP_TRY(hipMemcpyAsync(idx->d_stage, h_pos, m * sizeof(uint64_t), hipMemcpyHostToDevice, idx->stream));
+    return index_update_apply(idx, reinterpret_cast<const uint64_t*>(idx->d_stage), nullptr, m, h_v, m, head);
+}
+
+// The list of a hit pass (index_update_hits) back to the host.
+int index_update_hit_list(dawn_index* ws, size_t n, size_t cap, size_t n_hits, uint64_t* pos, uint32_t* req) {
+    const HitLayout H(n, cap);
+    const char* d = reinterpret_cast<const char*>(ws->d_stage);
+    DAWN_HIP_TRY(hipMemcpyAsync(pos, d + H.pos, n_hits * sizeof(uint64_t), hipMemcpyDeviceToHost, ws->stream));
+    DAWN_HIP_TRY(hipMemcpyAsync(req, d + H.req, n_hits * sizeof(uint32_t), hipMemcpyDeviceToHost, ws->stream));
+    DAWN_HIP_TRY(hipStreamSynchronize(ws->stream));
+    return DAWN_OK;
+}
+
 // Synthetic unit rows appended as pending rows: rows first_row.. of stream `seed`; labels first_id + i, or
 // (a shard of a sharded index) the global positions first_pos + i.
 int index_fill_async(dawn_index* idx, uint64_t seed, uint64_t first_row, size_t n, uint64_t first_id, bool ids_are_positions,
@@ -1635,6 +1786,42 @@ int dawn_index_remove(dawn_index* idx, size_t n, const uint64_t* ids, size_t* re
     return dawn::guarded([&] {
         DAWN_TRY(flush_adds(idx));  // (a staged row can be removed)
         return dawn::index_remove_single(idx, n, ids, removed);
+    });
+}
+
+// The gates (is_normalized, as add_batch; an id given twice) run on the host over the whole request before anything changes; the
+// request then goes down sorted by label with each entry's place in the caller's arrays.
+int dawn_index_update(dawn_index* idx, size_t n, const uint64_t* ids, const float* v, size_t* updated) {
+    if (!idx || (n && (!ids || !v))) return fail(DAWN_ERR_INVALID_ARG, "NULL argument");
+    if (updated) std::memset(updated, 0, n * sizeof(size_t));
+    if (n == 0) return DAWN_OK;
+    if (n >= 0xFFFFFFFFull) return fail(DAWN_ERR_UNSUPPORTED, "update: at most 2^32-2 ids per call");
+    return dawn::guarded([&] {
+        size_t bad = 0;
+        for (size_t o = 0; o < n;) {
+            const size_t f = dawn::host_first_not_normalized(v + o * dawn::EM, n - o);
+            if (f == n - o) break;
+            ++bad;
+            o += f + 1;
+        }
+        if (bad) return fail(DAWN_ERR_NOT_NORMALIZED, "Insert embedding is not normalized (%u of %zu rows)", (unsigned)bad, n);
+        std::vector<uint32_t> perm(n);
+        for (size_t i = 0; i < n; ++i) perm[i] = (uint32_t)i;
+        std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return ids[a] < ids[b]; });
+        std::vector<uint64_t> keys(n);
+        for (size_t j = 0; j < n; ++j) {
+            keys[j] = ids[perm[j]];
+            if (j && keys[j] == keys[j - 1])
+                return fail(DAWN_ERR_INVALID_ARG, "update: id %llu given twice (entries %u and %u)", (unsigned long long)keys[j],
+                            std::min(perm[j - 1], perm[j]), std::max(perm[j - 1], perm[j]));
+        }
+        DAWN_TRY(flush_adds(idx));  // (a staged row can be updated)
+        std::vector<uint64_t> cnt(n, 0);
+        DAWN_TRY(idx->shards ? dawn::sharded_update(idx, n, keys.data(), perm.data(), v, cnt.data())
+                             : dawn::index_update_single(idx, n, keys.data(), perm.data(), v, cnt.data()));
+        if (updated)
+            for (size_t j = 0; j < n; ++j) updated[perm[j]] = (size_t)cnt[j];
+        return DAWN_OK;
     });
 }
 

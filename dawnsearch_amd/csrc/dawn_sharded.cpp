@@ -534,6 +534,42 @@ int sharded_search_like(dawn_index* idx, size_t n, const uint64_t* ids, size_t c
     return DAWN_OK;
 }
 
+// Rows replaced in place by label: the hit pass runs on the root over the global labels in insertion order (S.d_gids) and yields
+// global positions; each maps to (shard, local row) by the dealing arithmetic (sharded handles never remove rows), and every shard
+// rewrites its rows and their shadow sub-tiles on its own device, issued by its own worker.
+int sharded_update(dawn_index* idx, size_t n, const uint64_t* keys, const uint32_t* perm, const float* v, uint64_t* cnt) {
+    ShardSet& S = *idx->shards;
+    if (S.size == 0) return DAWN_OK;
+    dawn_index* r = S.sh[0];  // the root shard's staging
+    DAWN_HIP_TRY(hipSetDevice(root_dev(S)));
+    size_t n_hits = 0, cap = 0;
+    DAWN_TRY(index_update_hits(r, S.d_gids, S.size, n, keys, perm, 0, cnt, &n_hits, &cap));
+    if (n_hits == 0) return DAWN_OK;
+    std::vector<uint64_t> pos(n_hits);
+    std::vector<uint32_t> req(n_hits);
+    DAWN_TRY(index_update_hit_list(r, n, cap, n_hits, pos.data(), req.data()));
+    std::vector<std::vector<uint64_t>> lpos(S.G);
+    std::vector<std::vector<float>> rows(S.G);
+    for (size_t e = 0; e < n_hits; ++e) {
+        if (pos[e] >= S.size) return fail(DAWN_ERR_HIP, "update: hit pass returned position %llu of %zu", (unsigned long long)pos[e], S.size);
+        int s;
+        size_t local;
+        S.locate((size_t)pos[e], &s, &local);
+        lpos[s].push_back(local);
+        rows[s].insert(rows[s].end(), v + (size_t)req[e] * EM, v + (size_t)(req[e] + 1) * EM);
+    }
+    const int rc = S.workers.run(S.G, [&](int g) -> int {
+        DAWN_HIP_TRY(hipSetDevice(S.dev[g]));
+        return index_update_rows_single(S.sh[g], lpos[g].size(), lpos[g].data(), rows[g].data());
+    });
+    if (rc != DAWN_OK) {  // some shards may hold new rows and others not: the index is emptied, as after a failed load
+        const std::string msg = last_error();
+        (void)sharded_clear(idx);
+        last_error() = msg;
+    }
+    return rc;
+}
+
 int sharded_set_option(dawn_index* idx, const char* name, int64_t value) {
     ShardSet& S = *idx->shards;
     const std::string n(name);

@@ -314,6 +314,15 @@ void index_append_abort(dawn_index* idx);   // drop the pending rows (I/O error 
 int index_clear(dawn_index* idx);           // size = 0 (load replaces the contents)
 // rows whose label is one of ids[0..n_ids) leave the index (compacted in place); *removed (may be NULL) = rows removed
 int index_remove_single(dawn_index* idx, size_t n_ids, const uint64_t* ids, size_t* removed);
+// Rows replaced in place by label (dawn_index_update).  keys [n]: the request's labels sorted, no repeats; perm[j]: the
+// place of keys[j] in the caller's arrays (its vector v[perm[j]]); cnt[j] (zeroed by the caller) = rows rewritten for keys[j].
+int index_update_single(dawn_index* idx, size_t n, const uint64_t* keys, const uint32_t* perm, const float* v, uint64_t* cnt);
+// ... its pieces for the sharded router: the hit pass over d_labels[0..n_rows) in ws's staging (list left on the device: *cap), the
+// list back to the host, and one shard's rows h_pos[e] (local positions) <- h_v[e]
+int index_update_hits(dawn_index* ws, const uint64_t* d_labels, size_t n_rows, size_t n, const uint64_t* keys, const uint32_t* perm,
+                      size_t apply_rows, uint64_t* cnt, size_t* n_hits, size_t* cap);
+int index_update_hit_list(dawn_index* ws, size_t n, size_t cap, size_t n_hits, uint64_t* pos, uint32_t* req);
+int index_update_rows_single(dawn_index* idx, size_t m, const uint64_t* h_pos, const float* h_v);
 int index_fill_async(dawn_index* idx, uint64_t seed, uint64_t first_row, size_t n, uint64_t first_id, bool ids_are_positions,
                      uint64_t first_pos);
 // Workspaces + filter shadows for the current rows and options, on idx->stream (callers synchronise).
@@ -358,6 +367,7 @@ int sharded_get_rows(dawn_index* idx, size_t first, size_t n, float* out_rows, u
 int sharded_get_by_label(dawn_index* idx, size_t n, const uint64_t* ids, float* out, size_t* counts);
 int sharded_search_like(dawn_index* idx, size_t n, const uint64_t* ids, size_t count, uint64_t* labels, float* distances,
                         size_t* found);
+int sharded_update(dawn_index* idx, size_t n, const uint64_t* keys, const uint32_t* perm, const float* v, uint64_t* cnt);
 int sharded_set_option(dawn_index* idx, const char* name, int64_t value);
 int sharded_memory(dawn_index* idx, uint64_t* rows_bytes, uint64_t* shadow_bytes, uint64_t* other_bytes);
 int sharded_stats(dawn_index* idx, uint64_t* searches, uint64_t* second, uint64_t* fallbacks, uint64_t* deepened,

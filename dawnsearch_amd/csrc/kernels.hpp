@@ -310,5 +310,32 @@ void launch_label_fixup(const uint32_t* d_missing, uint32_t B, uint32_t* d_found
 // even), and back (exact widening).
 void launch_rows_f32_to_bf16(const float* d_in, void* d_x, size_t first_row, size_t n_rows, hipStream_t stream);
 void launch_rows_bf16_to_f32(const void* d_x, size_t first_row, float* d_out, size_t n_rows, hipStream_t stream);
+// Rows replaced in place by label (index_update.hip, dawn_index_update).  hits: one read of d_labels[0..n) against the sorted,
+// duplicate-free request d_keys[0..n_keys); a row holding d_keys[j] adds 1 to d_cnt[j] (wave-aggregated) and appends (its
+// position, d_perm[j]) to the hit list d_hit_pos / d_hit_req while *d_total < cap (*d_total counts every hit: more than cap = the
+// list was too short).  The caller zeroes d_cnt and *d_total.  grid: workgroups at most.
+constexpr uint32_t UP_LDS_KEYS = 4096;  // request labels a workgroup keeps in LDS (more: an LDS fence of every k-th one, then L2)
+void launch_update_hits(const uint64_t* d_labels, size_t n, const uint64_t* d_keys, const uint32_t* d_perm, uint32_t n_keys,
+                        uint64_t* d_cnt, uint64_t* d_total, uint64_t* d_hit_pos, uint32_t* d_hit_req, size_t cap, int grid,
+                        hipStream_t stream);
+// scatter: hit e (< n_hits) whose request r = d_req[e] (d_req NULL: r = e) lies in [req_lo, req_hi) overwrites row d_pos[e]
+// (< n_rows) of the index d_x with d_v[r - req_lo] (f32; a bf16 index rounds to nearest even as launch_rows_f32_to_bf16) and sets
+// the row's 32-row sub-tile in d_dirty (1 bit per sub-tile).  dirty list: the set bits of d_dirty[0..n_words) -> sub-tile list
+// d_sub and 64-row tile list d_tile (any order; their lengths -> d_counts[0] / [1], which the caller zeroes).
+void launch_update_scatter(void* d_x, int rt, size_t n_rows, const uint64_t* d_pos, const uint32_t* d_req, size_t n_hits,
+                           const float* d_v, uint32_t req_lo, uint32_t req_hi, uint32_t* d_dirty, hipStream_t stream);
+void launch_update_dirty_list(const uint32_t* d_dirty, uint32_t n_words, uint32_t* d_sub, uint32_t* d_tile, uint32_t* d_counts,
+                              hipStream_t stream);
+// ... and the shadows of exactly those sub-tiles / tiles: the converters above for the listed ones d_list[0 .. *d_count) that lie
+// below prefix_rows (the shadow's converted prefix), rows >= n_valid as zeros — the same device code as the range converters.
+// max_list: an upper bound of *d_count (the grid).
+void launch_rows_to_i8s_list(const void* d_rows, int rt, void* d_shadow, void* d_meta, const uint32_t* d_list, const uint32_t* d_count,
+                             uint32_t max_list, size_t prefix_rows, size_t n_valid, hipStream_t stream, float levels = 127.0f);
+void launch_rows_to_i6s_list(const void* d_rows, int rt, int bits, void* d_shadow, void* d_meta, const uint32_t* d_list,
+                             const uint32_t* d_count, uint32_t max_list, size_t prefix_rows, size_t n_valid, hipStream_t stream);
+void launch_rows_to_f6s_list(const void* d_rows, int rt, void* d_shadow, void* d_meta, const uint32_t* d_list, const uint32_t* d_count,
+                             uint32_t max_list, size_t prefix_rows, size_t n_valid, hipStream_t stream);
+void launch_rows_f32_to_f16s_list(const float* d_rows, void* d_shadow, const uint32_t* d_tiles, const uint32_t* d_count, uint32_t max_list,
+                                  size_t prefix_rows, size_t n_valid, hipStream_t stream);
 
 }  // namespace dawn

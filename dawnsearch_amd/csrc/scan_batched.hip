@@ -1364,10 +1364,10 @@ int batched_init() {  // (on the current device: every shard of a multi-device h
 // f32 rows -> the filter's shadow copy (ROW_F16S, kernels.hpp): value * 2^8 rounded to nearest even, stored tile by
 // tile (64 rows, 48 KiB) in MFMA-fragment order.  One workgroup per tile: coalesced f32 reads, fragment-order
 // image assembled in LDS, linear coalesced write.  Rows >= n_valid of the last tile are written as zeros.
-__global__ __launch_bounds__(256) void rows_f32_to_f16s_kernel(const f32x4* __restrict__ x, half8* __restrict__ shadow,
-                                                              uint32_t first_tile, uint32_t n_valid) {
+// (the body is rows_f32_to_f16s_tile: the range kernel and the list kernel of dawn_index_update write the same bytes by construction)
+__device__ __forceinline__ void rows_f32_to_f16s_tile(const f32x4* __restrict__ x, half8* __restrict__ shadow, const uint32_t tile,
+                                                      uint32_t n_valid) {
     __shared__ __attribute__((aligned(16))) half4 img[TILE_ROWS * ROW_F4];  // 48 KiB, half4 units
-    const uint32_t tile = first_tile + blockIdx.x;
     const f32x4* src = x + (size_t)tile * (TILE_ROWS * ROW_F4);
     for (uint32_t c = threadIdx.x; c < TILE_ROWS * ROW_F4; c += 256) {
         const uint32_t row = c / ROW_F4, c4 = c % ROW_F4;  // f32x4 chunk c4 of tile row `row`: k = 4*c4..4*c4+3
@@ -1383,6 +1383,21 @@ __global__ __launch_bounds__(256) void rows_f32_to_f16s_kernel(const f32x4* __re
     for (uint32_t c = threadIdx.x; c < TILE_ROWS * ROW_C8; c += 256) dst[c] = im8[c];
 }
 
+__global__ __launch_bounds__(256) void rows_f32_to_f16s_kernel(const f32x4* __restrict__ x, half8* __restrict__ shadow,
+                                                              uint32_t first_tile, uint32_t n_valid) {
+    rows_f32_to_f16s_tile(x, shadow, first_tile + blockIdx.x, n_valid);
+}
+
+// The listed tiles list[0 .. *count) below end_tile (grid: an upper bound of *count)
+__global__ __launch_bounds__(256) void rows_f32_to_f16s_list_kernel(const f32x4* __restrict__ x, half8* __restrict__ shadow,
+                                                                   const uint32_t* __restrict__ list, const uint32_t* __restrict__ count,
+                                                                   uint32_t end_tile, uint32_t n_valid) {
+    if (blockIdx.x >= *count) return;
+    const uint32_t tile = list[blockIdx.x];
+    if (tile >= end_tile) return;
+    rows_f32_to_f16s_tile(x, shadow, tile, n_valid);
+}
+
 // Converts the tiles that hold rows [first_row, n_valid) of the f32 rows d_rows (row 0 = index row 0; the capacity
 // is padded to whole tiles) into d_shadow; rows below first_row in the first tile are converted again (same values).
 void launch_rows_f32_to_f16s(const float* d_rows, void* d_shadow, size_t first_row, size_t n_valid, hipStream_t stream) {
@@ -1390,6 +1405,14 @@ void launch_rows_f32_to_f16s(const float* d_rows, void* d_shadow, size_t first_r
     const uint32_t t0 = (uint32_t)(first_row / TILE_ROWS), t1 = (uint32_t)((n_valid + TILE_ROWS - 1) / TILE_ROWS);
     hipLaunchKernelGGL(rows_f32_to_f16s_kernel, dim3(t1 - t0), dim3(256), 0, stream, reinterpret_cast<const f32x4*>(d_rows),
                        reinterpret_cast<half8*>(d_shadow), t0, (uint32_t)n_valid);
+}
+
+void launch_rows_f32_to_f16s_list(const float* d_rows, void* d_shadow, const uint32_t* d_tiles, const uint32_t* d_count, uint32_t max_list,
+                                  size_t prefix_rows, size_t n_valid, hipStream_t stream) {
+    const uint32_t end_tile = (uint32_t)((prefix_rows + TILE_ROWS - 1) / TILE_ROWS);  // tiles the shadow holds
+    if (max_list == 0 || end_tile == 0) return;
+    hipLaunchKernelGGL(rows_f32_to_f16s_list_kernel, dim3(max_list), dim3(256), 0, stream, reinterpret_cast<const f32x4*>(d_rows),
+                       reinterpret_cast<half8*>(d_shadow), d_tiles, d_count, end_tile, (uint32_t)n_valid);
 }
 
 // queries -> the filter's 16-bit operand images: bf16 for a bf16 index (frt = ROW_BF16), scaled f16 otherwise

@@ -61,13 +61,13 @@ __device__ __forceinline__ uint32_t f6_encode(float v, float inv_s, float* deq) 
 // conversion: rows -> FP6 tiles + {1 / s, E} per 16-row tile.  One 256-thread block per 32 rows (two tiles); thread = (row r =
 // tid / 8, part = tid % 8) holds v[j] = elements 32 j + 4 part + {0..3}: the 8 threads of a row hold the 32 values of k-block j.
 // ------------------------------------------------------------------------------------------------
+// (the body is rows_to_f6s_pair: the range kernel and the list kernel of dawn_index_update write the same bytes by construction)
 template <int RT>
-__global__ __launch_bounds__(256) void rows_to_f6s_kernel(const void* __restrict__ xv, uint32_t* __restrict__ out,
-                                                           float2* __restrict__ meta, uint32_t first_pair, uint32_t n_valid) {
+__device__ __forceinline__ void rows_to_f6s_pair(const void* __restrict__ xv, uint32_t* __restrict__ out, float2* __restrict__ meta,
+                                                 const uint32_t pair, uint32_t n_valid) {  // rows 32 pair .. +31 = tiles 2 pair, 2 pair + 1
     constexpr int NC = 6;
     __shared__ float sh[4];
     __shared__ float sh_e[4][NC];
-    const uint32_t pair = first_pair + blockIdx.x;  // rows 32 pair .. +31 = tiles 2 pair, 2 pair + 1
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t r = tid >> 3, part = tid & 7;
     const uint32_t row = pair * 32u + r;
@@ -172,6 +172,23 @@ __global__ __launch_bounds__(256) void rows_to_f6s_kernel(const void* __restrict
     }
 }
 
+template <int RT>
+__global__ __launch_bounds__(256) void rows_to_f6s_kernel(const void* __restrict__ xv, uint32_t* __restrict__ out,
+                                                           float2* __restrict__ meta, uint32_t first_pair, uint32_t n_valid) {
+    rows_to_f6s_pair<RT>(xv, out, meta, first_pair + blockIdx.x, n_valid);
+}
+
+// The listed 32-row pairs list[0 .. *count) below end_pair (grid: an upper bound of *count)
+template <int RT>
+__global__ __launch_bounds__(256) void rows_to_f6s_list_kernel(const void* __restrict__ xv, uint32_t* __restrict__ out,
+                                                                float2* __restrict__ meta, const uint32_t* __restrict__ list,
+                                                                const uint32_t* __restrict__ count, uint32_t end_pair, uint32_t n_valid) {
+    if (blockIdx.x >= *count) return;
+    const uint32_t pair = list[blockIdx.x];
+    if (pair >= end_pair) return;
+    rows_to_f6s_pair<RT>(xv, out, meta, pair, n_valid);
+}
+
 void launch_rows_to_f6s(const void* d_rows, int rt, void* d_shadow, void* d_meta, size_t first_row, size_t n_valid, hipStream_t stream) {
     const uint32_t first_pair = (uint32_t)(first_row / 32);  // the 32-row pair holding first_row is re-quantised whole
     const uint32_t end_pair = (uint32_t)((n_valid + 31) / 32);
@@ -182,6 +199,18 @@ void launch_rows_to_f6s(const void* d_rows, int rt, void* d_shadow, void* d_meta
     else
         hipLaunchKernelGGL(rows_to_f6s_kernel<0>, dim3(end_pair - first_pair), dim3(256), 0, stream, d_rows,
                            reinterpret_cast<uint32_t*>(d_shadow), reinterpret_cast<float2*>(d_meta), first_pair, (uint32_t)n_valid);
+}
+
+void launch_rows_to_f6s_list(const void* d_rows, int rt, void* d_shadow, void* d_meta, const uint32_t* d_list, const uint32_t* d_count,
+                             uint32_t max_list, size_t prefix_rows, size_t n_valid, hipStream_t stream) {
+    const uint32_t end_pair = (uint32_t)((prefix_rows + 31) / 32);  // 32-row pairs the shadow holds
+    if (max_list == 0 || end_pair == 0) return;
+    if (rt == ROW_BF16)
+        hipLaunchKernelGGL(rows_to_f6s_list_kernel<1>, dim3(max_list), dim3(256), 0, stream, d_rows, reinterpret_cast<uint32_t*>(d_shadow),
+                           reinterpret_cast<float2*>(d_meta), d_list, d_count, end_pair, (uint32_t)n_valid);
+    else
+        hipLaunchKernelGGL(rows_to_f6s_list_kernel<0>, dim3(max_list), dim3(256), 0, stream, d_rows, reinterpret_cast<uint32_t*>(d_shadow),
+                           reinterpret_cast<float2*>(d_meta), d_list, d_count, end_pair, (uint32_t)n_valid);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -69,14 +69,14 @@ namespace dawn {
 // ------------------------------------------------------------------------------------------------
 // conversion: rows -> 6-bit sub-tiles + {1 / s, E} per sub-tile (rows_to_i8s_kernel with the packing above)
 // ------------------------------------------------------------------------------------------------
+// (the body is rows_to_i6s_sub: the range kernel and the list kernel of dawn_index_update write the same bytes by construction)
 template <int RT, int BITS>
-__global__ __launch_bounds__(256) void rows_to_i6s_kernel(const void* __restrict__ xv, uint32_t* __restrict__ out,
-                                                           float2* __restrict__ meta, uint32_t first_sub, uint32_t n_valid) {
+__device__ __forceinline__ void rows_to_i6s_sub(const void* __restrict__ xv, uint32_t* __restrict__ out, float2* __restrict__ meta,
+                                                const uint32_t sub, uint32_t n_valid) {
     typedef PackedShadow<BITS> PS;
     constexpr int NC = 6;  // candidate scales
     __shared__ float sh[4];
     __shared__ float sh_e[4][NC];
-    const uint32_t sub = first_sub + blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t r = tid >> 3, part = tid & 7;
     const uint32_t row = sub * 32u + r;
@@ -183,6 +183,23 @@ __global__ __launch_bounds__(256) void rows_to_i6s_kernel(const void* __restrict
     }
 }
 
+template <int RT, int BITS>
+__global__ __launch_bounds__(256) void rows_to_i6s_kernel(const void* __restrict__ xv, uint32_t* __restrict__ out,
+                                                           float2* __restrict__ meta, uint32_t first_sub, uint32_t n_valid) {
+    rows_to_i6s_sub<RT, BITS>(xv, out, meta, first_sub + blockIdx.x, n_valid);
+}
+
+// The listed sub-tiles list[0 .. *count) below end_sub (grid: an upper bound of *count)
+template <int RT, int BITS>
+__global__ __launch_bounds__(256) void rows_to_i6s_list_kernel(const void* __restrict__ xv, uint32_t* __restrict__ out,
+                                                                float2* __restrict__ meta, const uint32_t* __restrict__ list,
+                                                                const uint32_t* __restrict__ count, uint32_t end_sub, uint32_t n_valid) {
+    if (blockIdx.x >= *count) return;
+    const uint32_t sub = list[blockIdx.x];
+    if (sub >= end_sub) return;
+    rows_to_i6s_sub<RT, BITS>(xv, out, meta, sub, n_valid);
+}
+
 void launch_rows_to_i6s(const void* d_rows, int rt, int bits, void* d_shadow, void* d_meta, size_t first_row, size_t n_valid,
                         hipStream_t stream) {
     const uint32_t first_sub = (uint32_t)(first_row / 32);  // the sub-tile holding first_row is re-quantised whole
@@ -201,6 +218,25 @@ void launch_rows_to_i6s(const void* d_rows, int rt, int bits, void* d_shadow, vo
         else DAWN_I6_BUILD(0, 5);
     }
 #undef DAWN_I6_BUILD
+}
+
+void launch_rows_to_i6s_list(const void* d_rows, int rt, int bits, void* d_shadow, void* d_meta, const uint32_t* d_list,
+                             const uint32_t* d_count, uint32_t max_list, size_t prefix_rows, size_t n_valid, hipStream_t stream) {
+    const uint32_t end_sub = (uint32_t)((prefix_rows + 31) / 32);  // sub-tiles the shadow holds
+    if (max_list == 0 || end_sub == 0) return;
+    uint32_t* o = reinterpret_cast<uint32_t*>(d_shadow);
+    float2* mt = reinterpret_cast<float2*>(d_meta);
+#define DAWN_I6_LIST(RT_, BITS_)                                                                                           \
+    hipLaunchKernelGGL((rows_to_i6s_list_kernel<RT_, BITS_>), dim3(max_list), dim3(256), 0, stream, d_rows, o, mt, d_list, d_count, \
+                       end_sub, (uint32_t)n_valid)
+    if (rt == ROW_BF16) {
+        if (bits == 6) DAWN_I6_LIST(1, 6);
+        else DAWN_I6_LIST(1, 5);
+    } else {
+        if (bits == 6) DAWN_I6_LIST(0, 6);
+        else DAWN_I6_LIST(0, 5);
+    }
+#undef DAWN_I6_LIST
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -67,12 +67,11 @@ namespace dawn {
 // ------------------------------------------------------------------------------------------------
 // One 256-thread block per sub-tile; thread = (row r = tid / 8, part = tid % 8) handles float4 chunks part + 8j.
 // RT = 0: f32 rows; RT = 1: the fragment-ordered bf16 rows of a bf16 index (the int8 copy then shadows THOSE values).
+// (the body is rows_to_i8s_sub: the range kernel and the list kernel of dawn_index_update write the same bytes by construction)
 template <int RT>
-__global__ __launch_bounds__(256) void rows_to_i8s_kernel(const void* __restrict__ xv, uint32_t* __restrict__ out,
-                                                           float2* __restrict__ meta, uint32_t first_sub,
-                                                           uint32_t n_valid, float levels) {
+__device__ __forceinline__ void rows_to_i8s_sub(const void* __restrict__ xv, uint32_t* __restrict__ out, float2* __restrict__ meta,
+                                                const uint32_t sub, uint32_t n_valid, float levels) {
     __shared__ float sh[4];
-    const uint32_t sub = first_sub + blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t r = tid >> 3, part = tid & 7;
     const uint32_t row = sub * 32u + r;
@@ -139,6 +138,25 @@ __global__ __launch_bounds__(256) void rows_to_i8s_kernel(const void* __restrict
     }
 }
 
+template <int RT>
+__global__ __launch_bounds__(256) void rows_to_i8s_kernel(const void* __restrict__ xv, uint32_t* __restrict__ out,
+                                                           float2* __restrict__ meta, uint32_t first_sub,
+                                                           uint32_t n_valid, float levels) {
+    rows_to_i8s_sub<RT>(xv, out, meta, first_sub + blockIdx.x, n_valid, levels);
+}
+
+// The listed sub-tiles list[0 .. *count) below end_sub (grid: an upper bound of *count)
+template <int RT>
+__global__ __launch_bounds__(256) void rows_to_i8s_list_kernel(const void* __restrict__ xv, uint32_t* __restrict__ out,
+                                                                float2* __restrict__ meta, const uint32_t* __restrict__ list,
+                                                                const uint32_t* __restrict__ count, uint32_t end_sub,
+                                                                uint32_t n_valid, float levels) {
+    if (blockIdx.x >= *count) return;
+    const uint32_t sub = list[blockIdx.x];
+    if (sub >= end_sub) return;
+    rows_to_i8s_sub<RT>(xv, out, meta, sub, n_valid, levels);
+}
+
 
 // rt: ROW_F32 (f32 rows) or ROW_BF16 (fragment-ordered bf16 rows)
 void launch_rows_to_i8s(const void* d_rows, int rt, void* d_shadow, void* d_meta, size_t first_row, size_t n_valid,
@@ -152,6 +170,18 @@ void launch_rows_to_i8s(const void* d_rows, int rt, void* d_shadow, void* d_meta
     else
         hipLaunchKernelGGL(rows_to_i8s_kernel<0>, dim3(end_sub - first_sub), dim3(256), 0, stream, d_rows,
                            reinterpret_cast<uint32_t*>(d_shadow), reinterpret_cast<float2*>(d_meta), first_sub, (uint32_t)n_valid, levels);
+}
+
+void launch_rows_to_i8s_list(const void* d_rows, int rt, void* d_shadow, void* d_meta, const uint32_t* d_list, const uint32_t* d_count,
+                             uint32_t max_list, size_t prefix_rows, size_t n_valid, hipStream_t stream, float levels) {
+    const uint32_t end_sub = (uint32_t)((prefix_rows + 31) / 32);  // sub-tiles the shadow holds
+    if (max_list == 0 || end_sub == 0) return;
+    if (rt == ROW_BF16)
+        hipLaunchKernelGGL(rows_to_i8s_list_kernel<1>, dim3(max_list), dim3(256), 0, stream, d_rows, reinterpret_cast<uint32_t*>(d_shadow),
+                           reinterpret_cast<float2*>(d_meta), d_list, d_count, end_sub, (uint32_t)n_valid, levels);
+    else
+        hipLaunchKernelGGL(rows_to_i8s_list_kernel<0>, dim3(max_list), dim3(256), 0, stream, d_rows, reinterpret_cast<uint32_t*>(d_shadow),
+                           reinterpret_cast<float2*>(d_meta), d_list, d_count, end_sub, (uint32_t)n_valid, levels);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -76,6 +76,17 @@ class VectorIndex:
         check(lib.dawn_index_remove(self._h, ids.shape[0], _ptr(ids), C.byref(removed)))
         return removed.value
 
+    def update(self, ids, rows: np.ndarray):
+        """Replace in place the vector of every row labelled ids[b] with rows[b] (dawn_index_update): labels, positions and order
+        stay, and the index equals one built with the new vectors in place of the old.  All or nothing: a non-normalised row or
+        an id given twice changes nothing.  -> counts [n] int64: rows rewritten per id (0: the label is not in the index)."""
+        ids = np.ascontiguousarray(np.atleast_1d(np.asarray(ids, dtype=np.uint64)).ravel())
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, EM_LEN) if np.size(rows) else np.zeros((0, EM_LEN), np.float32)
+        assert rows.shape == (ids.shape[0], EM_LEN)
+        counts = np.zeros(ids.shape[0], dtype=np.uintp)
+        check(lib.dawn_index_update(self._h, ids.shape[0], _ptr(ids), _ptr(rows), _ptr(counts)))
+        return counts.astype(np.int64)
+
     def get(self, ids):
         """Index::get / count by label for an int or an array of them (dawn_index_get) -> (rows [n,384] f32: the row of each label —
         the earliest-added one holding it — zeros where the label is missing; counts [n] int64: rows holding each label)."""

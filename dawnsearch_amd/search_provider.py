@@ -133,8 +133,9 @@ class SearchProvider:
 
     def remove_pages(self, ids) -> int:
         """Drop pages (an id or ids) from the store and the index: their rows leave the index (dawn_index_remove), the
-        space they held counts again for `insert`, and a later `insert` of the same URL indexes it under a new rowid
-        (the re-crawl case).  Ids not stored are ignored.  -> pages removed."""
+        space they held counts again for `insert`, and a later `insert` of the same URL indexes it under a new rowid.
+        A re-crawled page that keeps its rowid goes through `refresh_pages` instead.  Ids not stored are ignored.
+        -> pages removed."""
         ids = [int(i) for i in np.atleast_1d(np.asarray(ids, dtype=np.uint64))]
         gone = sorted({i for i in ids if i in self._pages})
         if not gone:
@@ -145,6 +146,31 @@ class SearchProvider:
             if self._by_url.get(url) == id_:
                 del self._by_url[url]
         return len(gone)
+
+    def refresh_pages(self, pages: List[ExtractedPage], embeddings: np.ndarray):
+        """The re-crawl path: a page whose URL is stored keeps its rowid; its title, text and embedding are replaced and its
+        index row is rewritten in place (one dawn_index_update for all of them).  The other pages go through `insert_batch`.
+        Every embedding is gated before anything is stored; a URL given twice counts once (its last page wins).
+        -> (pages updated, pages inserted)."""
+        emb = np.ascontiguousarray(embeddings, dtype=np.float32)
+        if emb.ndim != 2 or emb.shape != (len(pages), EM_LEN):
+            raise ValueError("embeddings must be [len(pages), 384]")
+        for i in range(len(pages)):
+            if not is_normalized(emb[i]):
+                raise NotNormalizedError(-2, "Insert embedding is not normalized")
+        last = {p.url: i for i, p in enumerate(pages)}
+        old = [i for u, i in last.items() if u in self._by_url]
+        new = [i for u, i in last.items() if u not in self._by_url]
+        if self.page_count() + len(new) > MAX_LOCAL_PAGES:
+            raise DawnError(-1, "No space available")
+        if old:
+            ids = np.asarray([self._by_url[pages[i].url] for i in old], dtype=np.uint64)
+            self.index.update(ids, emb[old])
+            for id_, i in zip(ids.tolist(), old):
+                self._pages[id_] = (pages[i].url, pages[i].title, pages[i].text, emb[i].copy())
+        if new:
+            self.insert_batch([pages[i] for i in new], emb[new])
+        return len(old), len(new)
 
     # -- :127-153 ---------------------------------------------------------------------------------
     def fill_index_from_db(self) -> None:

@@ -100,6 +100,24 @@ int dawn_index_add_batch(dawn_index *idx, size_t n, const uint64_t *ids, const f
  * A captured hipGraph of dawn_index_search_device must be re-captured (as after add).  Sharded handles:
  * DAWN_ERR_UNSUPPORTED, nothing changed.  A device error part way leaves the index EMPTY (as a failed load does). */
 int dawn_index_remove(dawn_index *idx, size_t n, const uint64_t *ids, size_t *removed);
+/* Replaces, in place, the vector of every row holding ids[b] with v[b] (v: n rows of 384 f32) — the re-crawl of a page whose
+ * text changed.  Labels, positions, their order, size and capacity do not change.  updated [n] (NULL = not wanted): rows
+ * rewritten for ids[b]; 0 = the label is not in the index, which is not an error and changes nothing.  A label held by
+ * several rows rewrites all of them.  Any n; ids in any order.
+ * Afterwards the index is identical to one built by adding the same rows, in the same order, with the new vectors in place
+ * of the old: rows (a bf16 index rounds to nearest even, exactly as add does) and labels, every filter shadow (f16, int8,
+ * packed 5/6-bit with its per-sub-tile error headers, FP6), search results bit for bit (every search form), save files
+ * byte for byte.
+ * All or nothing: every v[b] must pass is_normalized, as in add_batch (else DAWN_ERR_NOT_NORMALIZED); an id given twice is
+ * DAWN_ERR_INVALID_ARG; NULL ids or v with n > 0 is DAWN_ERR_INVALID_ARG.  In each case nothing changes.  n = 0: DAWN_OK.
+ * Staged single-row adds are applied first (a staged row can be updated).
+ * Cost: one read of the label array (8 B per row) for the whole request, then work proportional to the rows rewritten: the
+ * rows, and the 32-row sub-tiles of the shadows that hold them.
+ * The call allocates nothing a search reads and moves no buffer: a hipGraph of dawn_index_search_device (or
+ * dawn_index_search_like_device) captured before an update replays exactly after it, on the new rows.
+ * Sharded handles: supported, with the results of the single-device index given the same calls.  A device error part way
+ * leaves the index EMPTY (as a failed remove or load does). */
+int dawn_index_update(dawn_index *idx, size_t n, const uint64_t *ids, const float *v, size_t *updated);
 
 /* Rows by label.  Labels are not unique (dawn_index_remove treats a label held by several rows as normal).  For a label L:
  * count(L) is the number of rows holding L; the row of L is the earliest-added row holding L — the lowest position, the row
